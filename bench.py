@@ -23,6 +23,13 @@ The other configurations are measured with --workload (same JSON line, same unit
           edge, 32-sphere checker                                     (configs[4], M4)
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg4|cfg5]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up the workload, warms up, times the K steps and prints the result line (with
+--dump-outputs, after writing the last timed step's outputs as DIR/<name>.npy).  Everything else the
+benchmark measures — the CPU baselines, the other configurations (the line's `workloads` record), the
+extras (index maintenance, sphere checker, RRT* k, single-query scans, the device RRT loop), the
+dominant kernel's isolated duration and the detail file — runs only with --full.
 """
 from __future__ import annotations
 
@@ -49,6 +56,8 @@ B_SE3 = {"f32": 28, "f64": 56}              # bytes per stored SE(3) state strea
 PMC_PROFILES = {w: [f"r6_{w}", f"r5_{w}", f"r4_{w}", f"r3_{w}"] for w in ("cfg3", "cfg2", "cfg4", "cfg5")}
 PMC_PROFILES["cfg5k"] = ["r6_cfg5k", "r5_cfg5k", "r4_cfg5k"]
 PMC_PROFILES["rrt_star"] = ["r6_rrt_star", "r5_rrt_star"]
+DETAIL_DEFAULT = os.path.join("bench_out", "bench_detail.json")  # --full's detail file
+DUMP_BYTES = 60_000_000  # --dump-outputs writes at most this much (a seeded row sample of larger outputs)
 DEFAULTS = {  # tree states, queries (samples / milestones / vertices) per GPU per step, k
     "cfg3": (1_000_000, 100_000, 10),
     "cfg2": (100_000, 100_000, 10),
@@ -147,9 +156,25 @@ def parse():
                     help="steps in flight for workloads whose batches are independent (cfg3, cfg2, cfg5 kNN): step i "
                          "runs on stream i %% lanes with its own NN / validator handles over the same tree, so the next "
                          "step's walk fills the CUs the current walk's tail leaves idle (1 = one stream)")
-    ap.add_argument("--detail", default=os.path.join("gpurun_out", "bench_detail.json"),
-                    help="file for the full record (the stdout line is the compact form); '' = none")
+    ap.add_argument("--detail", default=None,
+                    help=f"file for the full record (the stdout line is the compact form); default: {DETAIL_DEFAULT} "
+                         "with --full, none without; '' = none")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0's neighbour ids and "
+                         "distances, steered motions, validity bits) as DIR/<name>.npy, float64 / float32; at most "
+                         "64 MB (a fixed, seeded row sample of a larger output)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the CPU baselines, the extras, the single-query scans, the "
+                         "device RRT loop, the dominant kernel alone and the other configurations (--workloads), and "
+                         "write the detail file; without it these options are ignored and the run only sets up, warms "
+                         "up, times the steps and prints the line")
     a = ap.parse_args()
+    if not a.full:  # a plain run: the headline figure only
+        a.no_extras = a.no_cpu_baseline = True
+        a.single_query_reps = a.rrt_iters = a.rrt_star_queries = a.rrt_star_samples = 0
+        a.workloads = "none"
+    if a.detail is None:
+        a.detail = DETAIL_DEFAULT if a.full else ""
     if a.partition == "tree" and (a.workload not in ("cfg3", "cfg5") or a.bitstar_knn):
         ap.error("--partition tree is implemented for --workload cfg3 and the cfg5 radius mode")
     t, q, k = DEFAULTS[a.workload]
@@ -1142,6 +1167,28 @@ class Runner:
                 out["issue"] = iss
         return out
 
+    def outputs(self, L):
+        """what the caller of the timed step receives from lane L's last step, as host arrays
+        (--dump-outputs): neighbour ids and distances, the steered motions' endpoints (cfg3 / cfg2),
+        the motions' / edges' validity bits; cfg4: each milestone's neighbour ids, their count and
+        the edges' validity (entries past the count blanked)"""
+        torch, wl = self.torch, self.args.workload
+        if wl == "cfg4":
+            live = torch.arange(self.k, device=self.dev).unsqueeze(0) < self.cnt.unsqueeze(1)
+            t = {"ids": torch.where(live, L["ids"], -1), "count": self.cnt,
+                 "edge_valid": torch.where(live, self.evalid, 0)}
+        elif wl == "cfg5" and not self.k:  # nearestR: CSR offsets + the m = offsets[-1] entries
+            m = int(L["off"][-1].item())
+            t = {"offsets": L["off"], "ids": L["ids"][:m], "dist": L["dd"][:m], "valid": L["valid"][:m]}
+        else:
+            t = {"ids": L["ids"], "dist": L["dd"]}
+            if wl in ("cfg3", "cfg2") and not self.tree_mode:
+                t.update(steer_from=L["s_from"], steer_to=L["s_to"])
+            if wl != "cfg2":
+                t["valid"] = L["valid"]
+        return {name: x.cpu().numpy().astype(np.float32 if x.dtype == torch.uint8 else np.float64)
+                for name, x in t.items()}
+
     def close(self):
         """release the library handles (the next workload gets the HBM back)"""
         for ln in self.lanes:
@@ -1227,6 +1274,7 @@ def sub_args(args, spec):
     a.scaling = spec.get("scaling", "weak")
     a.tree, a.queries, a.k = DEFAULTS[a.workload]
     a.exact = False
+    a.dump_outputs = None
     if a.workload == "cfg4":
         # each PRM* batch grows the roadmap by 8,192 milestones: 2 + 5 batches keep it within 6 % of
         # the configuration's 10^6 vertices (20 + 10 would take it to 1.25 * 10^6)
@@ -1334,6 +1382,18 @@ def write_detail(line, path):
         return None
 
 
+def write_outputs(arrays, path):
+    """--dump-outputs: one .npy per array under `path`; when the arrays exceed DUMP_BYTES in all,
+    the same fraction of each one's rows, drawn once from default_rng(0) and kept in order"""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            keep = int(len(a) * DUMP_BYTES / total)
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def progress(msg):
     """a progress line on stderr (long default runs stay visibly alive)"""
     print(f"bench [{time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
@@ -1373,6 +1433,10 @@ def measure(args, torch, dev, local, rank, world, dist, stream, cpu_seconds):
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    run.dumped = None
+    if rank == 0 and getattr(args, "dump_outputs", None):  # the last timed step's lane
+        last = (args.steps - 1 if run.threaded else run.si - 1) % len(run.lanes)
+        run.dumped = run.outputs(run.lanes[last])
     if run.tree_mode and args.workload == "cfg3":  # motion checks of the samples whose nearest state this rank owns
         units += int(run.owned.item())
         run.m = int(run.last_owned.item())
@@ -1382,7 +1446,8 @@ def measure(args, torch, dev, local, rank, world, dist, stream, cpu_seconds):
     rp1 = run.radius_path_stats()
     c1 = run.counters()
     iso_ms = None
-    if len(run.lanes) > 1:  # the dominant kernel alone: a few steps on one lane, one at a time
+    # --full, the dominant kernel alone: a few steps on one lane, one at a time
+    if getattr(args, "full", False) and len(run.lanes) > 1:
         for _ in range(3):
             run.si = 0
             run.step()
@@ -1495,6 +1560,9 @@ def main():
     stream = torch.cuda.Stream(dev)  # a real (non-null) stream shared by torch events and the library
     wall0 = time.perf_counter()
     line, run = measure(args, torch, dev, local, rank, world, dist, stream, args.cpu_seconds)
+    if run.dumped:
+        write_outputs(run.dumped, args.dump_outputs)
+        run.dumped = None
 
     single = single_large = rrt = spheres = rrt_star = index = None
     if rank == 0 and not args.no_extras:

@@ -21,7 +21,7 @@ if [ "$MODE" = all ] || [ "$MODE" = test ]; then
     step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [ "$MODE" = all ] || [ "$MODE" = bench ]; then
-    step bench 600 python bench.py
+    step bench 600 python bench.py --full
 fi
 if [ "$MODE" = all ] || [ "$MODE" = prof ]; then
     TAG=${2:-r1}
