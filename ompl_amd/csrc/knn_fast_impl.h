@@ -818,11 +818,17 @@ __device__ __forceinline__ float box_tgap2(const float *bx, const float *q, int 
 // from a 16-bit copy.)
 template <int SP, int F, int K2, int G, bool QS>
 // (amdgpu_waves_per_eu(8), lists of up to 32 lanes: with the next super-tile's boxes in LDS the
-// walk fits 64 VGPRs and, with the scalar registers it then spills to VGPR lanes, 8 waves per SIMD
-// instead of 7 — cfg3's walk 1.022-1.028 against 1.046-1.049 ms isolated on one box, cfg2
-// unchanged; the boxes in LDS at 7 waves were slower, 8 waves with the boxes in registers spill to
-// scratch.  BIT*'s 64-lane lists keep the boxes in registers at 7 waves: 8 waves were no faster
-// (3.22-3.25 against 3.20-3.22 ms) and read 8 % more bytes, the LDS boxes at 7 waves were slower.)
+// walk fits 64 VGPRs and 8 waves per SIMD instead of 7 — cfg3's walk 1.022-1.028 against
+// 1.046-1.049 ms isolated on one box, cfg2 unchanged; the boxes in LDS at 7 waves were slower, 8
+// waves with the boxes in registers spill to scratch.  BIT*'s 64-lane lists keep the boxes in
+// registers at 7 waves: 8 waves were no faster (3.22-3.25 against 3.20-3.22 ms) and read 8 % more
+// bytes, the LDS boxes at 7 waves were slower.
+// Scalar registers: the K2 = 16 instance keeps 53 wave-uniform values in lanes of one VGPR (the
+// compiler's resource remarks: 78 SGPRs, 53 spilled, 64 VGPRs, no scratch).  They are the cold ones:
+// 34 are the bulk merge's lane-pattern masks, written once in front of the loop and read only inside
+// a bulk merge (about 1.5 per query), 19 are kernel arguments and prologue values read in the
+// epilogue; the only slot the tile loop reads is k2 - 1, once per offer.  What the loop pays for is
+// its instruction count per scan, so the scan's front is kept short: see scan_state.)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K2 == 64 ? 7 : 8))) void knn32_group_kernel(
     const float *__restrict__ rows, uint32_t n_pad, const uint32_t *__restrict__ ids, uint32_t ntiles,
     const float *__restrict__ tbox, const float *__restrict__ sbox, uint32_t nsuper, const float *__restrict__ mbox,
@@ -835,8 +841,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K2 == 64 ? 7
     // rotation first by a certified lower bound from the quaternion dot products (below)
     constexpr bool PK = SP == OMPL_GPU_SPACE_SE3 && G == 2;
     static_assert(G % 2 == 0 && K2 <= 64 && kMegaSupers == 64, "group walk shape");
-    __shared__ __attribute__((aligned(16))) float qrow[G * FS];
-    __shared__ __attribute__((aligned(16))) float qpair[PK ? 2 * FS : 2];  // (query 0, query 1) per coordinate
+    // the next super-tile's 32 tile boxes are staged in LDS (load_tbox below) when the record width allows
+    constexpr bool kLdsBox = BW % 8 == 0 && K2 < 64;
+    // one LDS block with the query rows first: the scans' reads of them then reach every row from one
+    // address register through the instruction's immediate offset (ds_read2_b64 spans 2 KB)
+    struct Lds {
+        alignas(16) float qpair[PK ? 2 * FS : 4];  // (query 0, query 1) per coordinate
+        alignas(16) float qrow[G * FS];
+        alignas(16) float tbs[kLdsBox ? kSuperTiles * BW : 4];  // the staged tile boxes
+        float slb[G][64], mlb[G][64];                            // the rounds' bounds (next_super, next_mega)
+    };
+    __shared__ Lds lds;
+    float (&qrow)[G * FS] = lds.qrow;
+    float (&qpair)[PK ? 2 * FS : 4] = lds.qpair;
     const int lane = threadIdx.x;
     const int half = lane >> 5;
     // XCD-aware group order: blocks b and b + 8 share an XCD (and its L2), so each XCD gets
@@ -879,7 +896,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K2 == 64 ? 7
     auto relaunder = [&]() {
         if constexpr (QS) asm volatile("" : "+s"(qoff));
     };
-    auto qscan = [&](int g) -> const float * { return &qrow[qoff + g * FS]; };
     // the lists (lane j = entry j) and their K2-th entries (wave-uniform); a padding query
     // gets threshold -inf so that it admits nothing and needs no tile
     uint64_t Lk[G];  // packed (distance, id) list entries (kpack)
@@ -1003,13 +1019,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K2 == 64 ? 7
     };
     auto scan_state = [&](const float (&x)[R], uint32_t id, int tin, const float (&lb)[GH]) {
         relaunder();
+        // the scan's own copy of the offset lives in a vector register: its (wave-uniform) LDS reads
+        // then share one address register and differ in the instruction's immediate offset, where a
+        // scalar offset costs a scalar add and a move to a vector register per read
+        uint32_t qv = qoff;
+        if constexpr (QS) asm volatile("" : "+v"(qv));
+        auto qscan = [&](int g) -> const float * { return &qrow[qv + g * FS]; };
         if constexpr (PK) {
             // both queries' translation terms and rotation lower bounds in one packed pass (the
             // translation in scan order: the same fp32 bits as the one-query form)
             bool on[2];
             on[0] = readlane_f(lb[0], tin) < td[0];
             on[1] = readlane_f(lb[0], tin + 32) < td[1];
-            const f2 *qp = reinterpret_cast<const f2 *>(&qpair[qoff]);
+            const f2 *qp = reinterpret_cast<const f2 *>(&qpair[qv]);
             f2 a = f2{x[0], x[0]} - qp[0];
             f2 t2 = a * a;
             a = f2{x[1], x[1]} - qp[1];
@@ -1028,7 +1050,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K2 == 64 ? 7
                 ++qscans;
                 const float clb = __builtin_amdgcn_sqrtf(fmaxf(fmaf(-2.f, fabsf(dd[g]), kq[g]), 0.f));
                 if (!__ballot(fmaf(w1, clb, wt[g]) < td[g])) continue;
-                const float c2 = chord2(x + 3, qscan(g) + 4);
+                // the quaternion as values defined here: chord2's (p, p) operand pairs are then built
+                // for the scans that pass the bound above, not hoisted in front of every scan
+                float p[4] = {x[3], x[4], x[5], x[6]};
+                asm volatile("" : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]));
+                const float c2 = chord2(p, qscan(g) + 4);
                 const float c = __builtin_amdgcn_sqrtf(c2);
                 if (!__ballot(fmaf(w1, c, wt[g]) < td[g])) continue;
                 offer(g, fmaf(w1, chord_theta(c, c2), wt[g]), id);
@@ -1087,12 +1113,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K2 == 64 ? 7
     // popped later is skipped when the thresholds have tightened past all of its bounds since
     // its round, before its 32 tile boxes are loaded and tested.  Kept in LDS, not VGPRs: G
     // values live across the whole walk cost 29 VGPRs (69 -> 98, 7 -> 5 waves per SIMD)
-    __shared__ float slb[G][64];
+    float (&slb)[G][64] = lds.slb;
     bool first_round = true;  // the neighbourhood's three are always visited
     // mega-tiles (kMegaSupers super-tiles each): a round tests 64 mega boxes; a super-tile round
     // then covers the 64 super-tiles of one passing mega.  A popped mega is re-checked against the
     // tightened thresholds by its round bounds (mlb, LDS) like a popped super-tile.
-    __shared__ float mlb[G][64];
+    float (&mlb)[G][64] = lds.mlb;
     uint32_t mb = 0, mbase = 0;
     uint64_t mm = 0;
     auto next_mega = [&]() -> int {
@@ -1199,8 +1225,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K2 == 64 ? 7
     // current thresholds before it is scanned.  (Measured: 1.27-1.29 -> 1.25-1.26 ms on cfg3.)
     // the next super-tile's 32 tile boxes: staged in LDS by LDS-DMA (BW / 8 loads of 1 KB, no
     // registers held across the scans) when the record width allows, else in registers
-    constexpr bool kLdsBox = BW % 8 == 0 && K2 < 64;
-    __shared__ __attribute__((aligned(16))) float tbs[kLdsBox ? kSuperTiles * BW : 4];
+    float (&tbs)[kLdsBox ? kSuperTiles * BW : 4] = lds.tbs;
     float bx[kLdsBox ? 1 : BW];
     auto load_tbox = [&](uint32_t sv) {
         if constexpr (kLdsBox) {
