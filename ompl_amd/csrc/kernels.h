@@ -92,11 +92,6 @@ constexpr int kSuperTiles = 32;
 // over a 10^7-state store tests 77 mega boxes and then only the super-tiles of the megas that
 // pass, instead of all 4,883 super-tile boxes (one lane per box, 64 per round)
 constexpr int kMegaSupers = 64;
-// queries per wave in the group walk.  Measured on MI355X (k=10, 10^5 queries, k-d tiles):
-// SE3 10^6 states G=2 2.09 ms, G=4 2.18 ms; R^6 10^5 states G=2 2.20 ms, G=4 1.50 ms.  (With
-// Morton-run tiles, SE3: G=8 4.4 ms, G=4 3.5 ms, G=2 3.2 ms; packed two-query math 3.7 ms.)
-// The walk is a chain of dependent memory round trips per wave, so narrower waves win where
-// the walk is long (SE3, 10^6 states), wider ones where the store is small and L2-resident.
 template <int SP>
 // queries per wave of the culled kNN walk.  Round 1 measured SE3 G = 2 / 4 / 8 -> 2.04 / 1.41 / 1.73
 // ms and R^6 G = 4 / 8 -> 1.01 / 0.70 ms; on round 4's walk (pipelined, packed keys, k-d
@@ -145,7 +140,9 @@ struct SortedStore {
     uint32_t main_live = 0, tail_t0 = 0, tail_cap_tiles = 0;
     uint64_t main_covered = 0, covered = 0, removed = 0;
     size_t cap_pos = 0, cap_nodes = 0, cap_inv = 0;  // allocated positions / nodes / inv entries
-    uint32_t *qcount = nullptr;  // [pad_tiles + 1] per-tile query counts of the home-key counting sort
+    // bins of the query sort by home tile (knn_fast_impl.h home_bins): counts | start | block sums,
+    // laid out for cap_pos / kCullTile tiles when allocated, the counts zero between calls
+    uint32_t *qcount = nullptr;
     // KinematicChain: the joint positions as 16-bit fixed point, two per word, F / 2 words per
     // position (chain_q16_code), re-encoded from `rows` when the store changed (gen != gen16)
     // SE3 (the radius walk): the 7 coordinates as 16-bit codes over q16 (4 words per position);

@@ -1,6 +1,6 @@
 // knn_fast.hip — dispatch of the exact batched kNN (fp32 screen + fp64 certificate).
 // The kernels and their host orchestration live in knn_fast_impl.h, instantiated per
-// space in knn_fast_se3.hip / knn_fast_so3.hip / knn_fast_rv.hip.
+// space in knn_fast_se3.hip / knn_fast_so3.hip / knn_fast_rv.hip / knn_fast_chain.hip.
 #include "knn_fast_impl.h"
 
 namespace ompl_amd {

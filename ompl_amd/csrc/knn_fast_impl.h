@@ -37,7 +37,7 @@
 //                       polynomial <= 1.1e-7, with its fp32 evaluation <= 1.8e-7)
 //   SO3 rotation      : 1.1 sqrt(2 * 6u) + 1e-6 + 4.5e-5 (the chunked screen keeps acos(|dot|))
 #pragma once
-// Included by one translation unit per space (knn_fast_{se3,so3,rv}.hip) so that the
+// Included by one translation unit per space (knn_fast_{se3,so3,rv,chain}.hip) so that the
 // template instantiations compile in parallel; knn_fast.hip holds the dispatch.
 #include <hip/hip_runtime.h>
 #include <cstring>  // (rocPRIM block primitives need memset declared)
@@ -223,12 +223,15 @@ __global__ void query_rows_kernel(const double *__restrict__ qf, uint32_t nq, Fa
 }
 
 // queries sorted by home tile.  Home-tile keys (< bins = the k-d tiles) take a counting sort over
-// the whole grid — a count kernel whose atomicAdd also hands each query its slot inside its tile,
-// a one-block exclusive scan of the bins, a scatter: three launches; queries of one tile land in
-// any order, which only changes how the walk's groups are formed, never a result.  Wider keys
-// (32-bit Morton codes when there is no k-d tree; the tail's Morton / home keys) are counted by
-// their top 16 bits (key >> shift): 65,536 cells of the Morton curve, order inside a cell
-// arbitrary — a coarser curve, still exact (tile order never changes a result).  (Measured and
+// the whole grid — a count whose atomicAdd also hands each query its slot inside its tile (fused
+// into query_rows_kernel), an exclusive scan of the bins, a placement: three launches
+// (sort_queries); queries of one tile land in any order, which only changes how the walk's groups
+// are formed, never a result.  Wider keys (32-bit Morton codes when there is no k-d tree; the
+// tail's Morton / home keys) are counted by their top 16 bits (key >> shift): 65,536 cells of the
+// Morton curve, order inside a cell arbitrary — a coarser curve, still exact (tile order never
+// changes a result) — over scratch bins: a memset and four launches (sort_home_keys: count, scan,
+// scan of the block totals, scatter).  The scan zeroes the counts it read, which only the
+// persistent bins need; for the scratch bins that store is spent to keep one scan kernel.  (Measured and
 // rejected in round 3: a one-block LDS counting sort, one CU doing every atomic and write: nn
 // phase 1.41 -> 1.48 ms.)
 __global__ void home_count_kernel(const uint32_t *__restrict__ keys, uint32_t nq, uint32_t *__restrict__ cnt,
@@ -236,18 +239,38 @@ __global__ void home_count_kernel(const uint32_t *__restrict__ keys, uint32_t nq
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < nq) slot[i] = atomicAdd(&cnt[keys[i] >> shift], 1u);
 }
-// exclusive scan of the bin counts in two levels: each block of 1,024 bins in place (coalesced,
-// one block scan) with its total to bsum, then the block totals by one block; the scatter adds
-// both.  (A single block looping over the 156 k bins of a 10^7-state store took 257 us.)
-__global__ __launch_bounds__(1024) void home_scan_kernel(uint32_t *__restrict__ cnt, uint32_t bins,
-                                                         uint32_t *__restrict__ bsum) {
+// The sort's bins, one layout for both callers: counts | start | block sums over a bin *capacity*
+// (cnt[] and start[] padded to nb blocks of 1,024 bins, a total per block, + 1).  A call may use
+// fewer bins — it scans only their blocks — and still finds the three parts where the capacity put
+// them, so no call ever meets an earlier call's start[] or bsum words among its counts.
+struct HomeBins {
+    uint32_t *cnt, *start, *bsum;
+    uint32_t nb;   // blocks of 1,024 bins
+    size_t words;  // of the whole array
+};
+inline HomeBins home_bins(uint32_t *base, uint32_t cap) {  // base == nullptr: the size only
+    const uint32_t nb = (cap + 1023) / 1024;
+    const size_t pad = (size_t)nb * 1024;
+    return {base, base ? base + pad : nullptr, base ? base + 2 * pad : nullptr, nb, 2 * pad + nb + 1};
+}
+inline size_t home_bins_words(uint32_t cap) { return home_bins(nullptr, cap).words; }
+// exclusive scan of the bin counts in two levels: each block of 1,024 counts into prefixes in
+// start[] (coalesced, one block scan), its total to bsum and the counts read back to zero; then
+// the block totals, by home_scan_blocks_kernel or inside home_place_kernel; the scatter adds both.
+// (A single block looping over the 156 k bins of a 10^7-state store took 257 us.)
+__global__ __launch_bounds__(1024) void home_bins_scan_kernel(uint32_t *__restrict__ cnt, uint32_t bins,
+                                                              uint32_t *__restrict__ start,
+                                                              uint32_t *__restrict__ bsum) {
     using BlockScan = rocprim::block_scan<uint32_t, 1024>;
     __shared__ typename BlockScan::storage_type sh;
     const uint32_t b = blockIdx.x * 1024 + threadIdx.x;
     const uint32_t c = b < bins ? cnt[b] : 0u;
     uint32_t pre = 0, tot = 0;
     BlockScan().exclusive_scan(c, pre, 0u, tot, sh);
-    if (b < bins) cnt[b] = pre;
+    if (b < bins) {
+        start[b] = pre;
+        cnt[b] = 0u;  // ready for the next call
+    }
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 __global__ __launch_bounds__(1024) void home_scan_blocks_kernel(uint32_t *__restrict__ bsum, uint32_t nb) {
@@ -275,28 +298,21 @@ __global__ void home_scatter_kernel(const uint32_t *__restrict__ keys, const uin
     perm[p] = idx[i];
 }
 inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-// The home-key sort over the store's persistent bins (SortedStore::qcount: counts | start | block
-// sums), which stay zero between calls — zeroed once when allocated, and by home_bins_scan_kernel
-// as it reads them: query_rows_kernel counts (slot = its atomicAdd), the scan turns each block of
-// 1,024 counts into exclusive prefixes in start[] with the block's total in bsum, and
-// home_place_kernel puts each query at (prefix of the block totals) + start + slot, writing its
-// key and its fp32 row in sorted order.  Three launches instead of six (count, two scans, scatter,
-// row gather, and the zeroing of the bins).
-__global__ __launch_bounds__(1024) void home_bins_scan_kernel(uint32_t *__restrict__ cnt, uint32_t bins,
-                                                              uint32_t *__restrict__ start,
-                                                              uint32_t *__restrict__ bsum) {
-    using BlockScan = rocprim::block_scan<uint32_t, 1024>;
-    __shared__ typename BlockScan::storage_type sh;
-    const uint32_t b = blockIdx.x * 1024 + threadIdx.x;
-    const uint32_t c = b < bins ? cnt[b] : 0u;
-    uint32_t pre = 0, tot = 0;
-    BlockScan().exclusive_scan(c, pre, 0u, tot, sh);
-    if (b < bins) {
-        start[b] = pre;
-        cnt[b] = 0u;  // ready for the next call
+// carves a workspace into consecutive 256-byte-aligned parts: take() returns the part's byte
+// offset, `off` ends as the total
+struct Carver {
+    size_t off = 0;
+    size_t take(size_t bytes) {
+        const size_t o = off;
+        off += align_up(bytes);
+        return o;
     }
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
+};
+// The home-key sort over the store's persistent bins (SortedStore::qcount, laid out for the store's
+// tile capacity), zero between calls — zeroed when allocated, then by the scan: query_rows_kernel
+// counts (slot = its atomicAdd), the scan fills start[] and bsum, and home_place_kernel puts each
+// query at (prefix of the block totals) + start + slot, writing its key and its fp32 row in sorted
+// order.  Three launches instead of six (count, two scans, scatter, row gather, zeroing the bins).
 template <int FS>
 __global__ __launch_bounds__(256) void home_place_kernel(const uint32_t *__restrict__ keys,
                                                          const uint32_t *__restrict__ slot, uint32_t nq,
@@ -334,46 +350,30 @@ __global__ __launch_bounds__(256) void home_place_kernel(const uint32_t *__restr
 #pragma unroll
     for (int f = 0; f < FS; ++f) q32[(size_t)p * FS + f] = q32u[(size_t)i * FS + f];
 }
-// words of SortedStore::qcount for `tiles` bins: counts and start padded to 1,024, the block sums
-inline size_t home_bins_words(uint32_t tiles) {
-    const size_t nb = ((size_t)tiles + 1023) / 1024;
-    return 2 * nb * 1024 + nb + 1;
-}
 constexpr int kCountBitsMax = 16;  // counting-sort cells of a wide key: its top 16 bits
-// scratch of sort_home_keys without a caller's bin array: the slots, then 2^16 bins padded to
-// 1,024 and their block sums
+// scratch of sort_home_keys: the slots, then bins for 2^16 cells
 inline size_t home_sort_bytes(uint32_t n) {
-    return align_up(4ull * std::max<uint32_t>(n, 1)) + 4ull * ((1u << kCountBitsMax) / 1024 * 1025 + 1);
+    return align_up(4ull * std::max<uint32_t>(n, 1)) + 4ull * home_bins_words(1u << kCountBitsMax);
 }
-// (keys, idx) -> (keys2, perm) ordered by key >> shift; shift = 0 with a caller's bin array
-// (qcount, bins > every key: the k-d home tiles), else the key's top kCountBitsMax of key_bits
+// wide keys: (keys, idx) -> (keys2, perm) ordered by the key's top kCountBitsMax of key_bits, over
+// bins of its own in the scratch, cleared here
 inline hipError_t sort_home_keys(char *ws, size_t ws_bytes, const uint32_t *keys, uint32_t *keys2,
-                                 const uint32_t *idx, uint32_t *perm, uint32_t nq, int key_bits, hipStream_t st,
-                                 uint32_t *qcount = nullptr, uint32_t bins = 0, bool zeroed = false) {
+                                 const uint32_t *idx, uint32_t *perm, uint32_t nq, int key_bits, hipStream_t st) {
     // the counting sort (measured 0.081-0.083 ms against 0.113-0.115 ms for a radix sort of the
     // nn phase outside the walk on cfg3)
     if (nq == 0) return hipSuccess;
-    if (ws_bytes < 4ull * nq) return hipErrorInvalidValue;
+    if (ws_bytes < home_sort_bytes(nq)) return hipErrorInvalidValue;
     uint32_t *slot = (uint32_t *)ws;
-    int shift = 0;
-    if (!(qcount && bins)) {  // own bins after the slots: the key's top bits
-        if (ws_bytes < home_sort_bytes(nq)) return hipErrorInvalidValue;
-        shift = std::max(0, key_bits - kCountBitsMax);
-        bins = (uint32_t)((((uint64_t)1 << key_bits) - 1) >> shift) + 1;
-        qcount = (uint32_t *)(ws + align_up(4ull * nq));
-        zeroed = false;
-    }
-    if (!zeroed) {  // (query_rows_kernel zeroes the bins when the caller listed them)
-        const hipError_t e = hipMemsetAsync(qcount, 0, 4ull * bins, st);
-        if (e != hipSuccess) return e;
-    }
-    const uint32_t nb = (bins + 1023) / 1024;
-    uint32_t *bsum = qcount + nb * 1024;  // qcount holds the bins padded to 1,024, then the block sums
-    hipLaunchKernelGGL(home_count_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, keys, nq, qcount, slot, shift);
-    hipLaunchKernelGGL(home_scan_kernel, dim3(nb), dim3(1024), 0, st, qcount, bins, bsum);
-    hipLaunchKernelGGL(home_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, bsum, nb);
-    hipLaunchKernelGGL(home_scatter_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, keys, idx, slot, nq, qcount,
-                       bsum, keys2, perm, shift);
+    const int shift = std::max(0, key_bits - kCountBitsMax);
+    const uint32_t bins = (uint32_t)((((uint64_t)1 << key_bits) - 1) >> shift) + 1;
+    const HomeBins h = home_bins((uint32_t *)(ws + align_up(4ull * nq)), bins);
+    const hipError_t e = hipMemsetAsync(h.cnt, 0, 4ull * bins, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(home_count_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, keys, nq, h.cnt, slot, shift);
+    hipLaunchKernelGGL(home_bins_scan_kernel, dim3(h.nb), dim3(1024), 0, st, h.cnt, bins, h.start, h.bsum);
+    hipLaunchKernelGGL(home_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, h.bsum, h.nb);
+    hipLaunchKernelGGL(home_scatter_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, keys, idx, slot, nq, h.start,
+                       h.bsum, keys2, perm, shift);
     return hipGetLastError();
 }
 
@@ -386,31 +386,59 @@ __global__ void query_gather_kernel(const float *__restrict__ q32u, const uint32
     q32[t] = q32u[(size_t)perm[qs] * FS + f];
 }
 
+// the query sort's part of a batch workspace, in front of the kNN and the radius layouts: keys and
+// order before / after the sort, its scratch (slots, + bins for wide keys), the fp32 rows likewise
+struct QueryLayout {
+    size_t keys, keys2, idx, perm, cub, cub_bytes, q32u, q32;
+};
+inline QueryLayout query_layout(Carver &c, uint32_t nq, int FS) {
+    QueryLayout L{};
+    L.keys = c.take(4ull * nq);
+    L.keys2 = c.take(4ull * nq);
+    L.idx = c.take(4ull * nq);
+    L.perm = c.take(4ull * nq);
+    L.cub_bytes = home_sort_bytes(nq);
+    L.cub = c.take(L.cub_bytes);
+    L.q32u = c.take(4ull * nq * FS);
+    L.q32 = c.take(4ull * nq * FS);
+    return L;
+}
+struct QueryBufs {
+    uint32_t *keys, *keys2, *idx, *perm;
+    char *cub;
+    size_t cub_bytes;
+    float *q32u, *q32;
+};
+inline QueryBufs query_bufs(char *ws, const QueryLayout &L) {
+    return {(uint32_t *)(ws + L.keys), (uint32_t *)(ws + L.keys2), (uint32_t *)(ws + L.idx), (uint32_t *)(ws + L.perm),
+            ws + L.cub, L.cub_bytes, (float *)(ws + L.q32u), (float *)(ws + L.q32)};
+}
+
 // queries ordered by key for the walks: the home-key sort when the store has a k-d tree
 // (home_keys), else the counting sort on the Morton key's top bits + a row gather
 template <int SP, int F>
 hipError_t sort_queries(const double *qf64, uint32_t nq, const FastBounds &b, const SortedStore *ss, bool home_keys,
-                        char *ws, size_t ws_bytes, float *q32u, uint32_t *keys, uint32_t *keys2, uint32_t *idx,
-                        uint32_t *perm, float *q32, hipStream_t st, const KdNode *nodes, uint32_t ntiles) {
+                        const QueryBufs &q, hipStream_t st, const KdNode *nodes, uint32_t ntiles) {
     constexpr int FS = Geo<SP, F>::FS;
     const dim3 b256(256);
     if (home_keys) {
+        // the bins' layout is that of the tile capacity they were allocated for (sorted_alloc)
+        const HomeBins h = home_bins(ss->qcount, (uint32_t)(ss->cap_pos / kCullTile));
         const uint32_t bins = ss->kd_tiles, nb = (bins + 1023) / 1024;
-        uint32_t *cnt = ss->qcount, *start = cnt + (size_t)nb * 1024, *bsum = start + (size_t)nb * 1024;
-        uint32_t *slot = (uint32_t *)ws;
-        if (ws_bytes < 4ull * nq) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((query_rows_kernel<SP, F>), dim3((nq + 255) / 256), b256, 0, st, qf64, nq, b, q32u, keys, idx,
-                           nodes, ntiles, cnt, slot);
-        hipLaunchKernelGGL(home_bins_scan_kernel, dim3(nb), dim3(1024), 0, st, cnt, bins, start, bsum);
-        hipLaunchKernelGGL((home_place_kernel<FS>), dim3((nq + 255) / 256), b256, 0, st, keys, slot, nq, start, bsum,
-                           nb, q32u, keys2, perm, q32);
+        uint32_t *slot = (uint32_t *)q.cub;
+        if (q.cub_bytes < 4ull * nq || nb > h.nb) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((query_rows_kernel<SP, F>), dim3((nq + 255) / 256), b256, 0, st, qf64, nq, b, q.q32u, q.keys,
+                           q.idx, nodes, ntiles, h.cnt, slot);
+        hipLaunchKernelGGL(home_bins_scan_kernel, dim3(nb), dim3(1024), 0, st, h.cnt, bins, h.start, h.bsum);
+        hipLaunchKernelGGL((home_place_kernel<FS>), dim3((nq + 255) / 256), b256, 0, st, q.keys, slot, nq, h.start,
+                           h.bsum, nb, q.q32u, q.keys2, q.perm, q.q32);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL((query_rows_kernel<SP, F>), dim3((nq + 255) / 256), b256, 0, st, qf64, nq, b, q32u, keys, idx,
-                       nodes, ntiles, nullptr, nullptr);
-    const hipError_t e = sort_home_keys(ws, ws_bytes, keys, keys2, idx, perm, nq, 32, st);
+    hipLaunchKernelGGL((query_rows_kernel<SP, F>), dim3((nq + 255) / 256), b256, 0, st, qf64, nq, b, q.q32u, q.keys,
+                       q.idx, nodes, ntiles, nullptr, nullptr);
+    const hipError_t e = sort_home_keys(q.cub, q.cub_bytes, q.keys, q.keys2, q.idx, q.perm, nq, 32, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((query_gather_kernel<FS>), dim3((nq * FS + 255) / 256), b256, 0, st, q32u, perm, nq, q32);
+    hipLaunchKernelGGL((query_gather_kernel<FS>), dim3((nq * FS + 255) / 256), b256, 0, st, q.q32u, q.perm, nq, q.q32);
     return hipGetLastError();
 }
 
@@ -662,9 +690,6 @@ __device__ __forceinline__ uint32_t readlane_u(uint32_t v, int l) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, l);
 }
 // value of lane - 1 (wave-wide DPP shift); lane 0 receives `first`
-__device__ __forceinline__ float shr1_f(float v, float first) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(first), __float_as_int(v), 0x138, 0xF, 0xF, false));
-}
 __device__ __forceinline__ uint32_t shr1_u(uint32_t v, uint32_t first) {
     return (uint32_t)__builtin_amdgcn_update_dpp((int)first, (int)v, 0x138, 0xF, 0xF, false);
 }
@@ -721,12 +746,6 @@ __device__ __forceinline__ uint64_t readlane_k(uint64_t v, int l) {
 }
 __device__ __forceinline__ uint64_t shr1_k(uint64_t v, uint64_t first) {
     return ((uint64_t)shr1_u((uint32_t)(v >> 32), (uint32_t)(first >> 32)) << 32) | shr1_u((uint32_t)v, (uint32_t)first);
-}
-__device__ __forceinline__ uint64_t shfl_k(uint64_t v, int src) {
-    return ((uint64_t)(uint32_t)__shfl((int)(v >> 32), src) << 32) | (uint32_t)__shfl((int)v, src);
-}
-__device__ __forceinline__ uint64_t shfl_xor_k(uint64_t v, int j) {
-    return ((uint64_t)(uint32_t)__shfl_xor((int)(v >> 32), j) << 32) | (uint32_t)__shfl_xor((int)v, j);
 }
 // the value of lane ^ j without the LDS crossbar (ds_bpermute waits on lgkmcnt at every stage of
 // a serial network): DPP inside a row of 16 — quad_perm for j = 1, 2, row_shl / row_shr by 4 for
@@ -798,17 +817,6 @@ __device__ __forceinline__ void lds_reads_done() {
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
     asm volatile("" ::: "memory");
-}
-
-// translation part of box_lb<SE3>: the squared gap of query row q to box bx
-__device__ __forceinline__ float box_tgap2(const float *bx, const float *q, int NB) {
-    float tg = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float g = gap(bx[c] - q[c], q[c] - bx[NB + c]);
-        tg = fmaf(g, g, tg);
-    }
-    return tg;
 }
 
 // K2: lanes per query in the output (16 / 32 / 64); k2 <= K2: the list length the walk keeps
@@ -1538,7 +1546,6 @@ __global__ __launch_bounds__(64 * WPB) void knn32_wave_scan_kernel(const float *
 // vanish for stores whose coordinates are all tiny.
 constexpr double kFltMin = 1.1754943508222875e-38;
 
-// eta: |norm^2 - 1| of the stored quaternions (largest) plus the query's (SE3)
 // Merge of the S chunk lists of a query (each sorted, K2 <= 64 entries) into one list of the
 // K2 best by (distance, id), written over chunk 0's slots: a wave per query, one bitonic merge
 // per further chunk (wave_merge_sorted_k).  The culled chain scan's lists then take the wave
@@ -2515,34 +2522,23 @@ FastPlan fast_plan(const DevSpace &sp, uint32_t nq, uint32_t k, uint64_t n_end, 
     return p;
 }
 
+// fp32 row width of a query (Geo::FS)
+inline int query_row_width(const DevSpace &sp, const FeatGeom &g) { return sp.kind == OMPL_GPU_SPACE_SE3 ? 8 : g.F; }
 
 struct FastLayout {
-    size_t keys, keys2, idx, perm, cub, q32u, q32, pd, pi, fail, tau, total;
-    size_t cub_bytes;
+    QueryLayout q;
+    size_t pd, pi, fail, tau, total;
 };
 
 FastLayout fast_layout(const DevSpace &sp, const FeatGeom &g, const FastPlan &p, uint32_t nq) {
     FastLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t b) {
-        size_t o = off;
-        off += align_up(b);
-        return o;
-    };
-    L.keys = take(4ull * nq);
-    L.keys2 = take(4ull * nq);
-    L.idx = take(4ull * nq);
-    L.perm = take(4ull * nq);
-    L.cub_bytes = home_sort_bytes(nq);  // the counting sort's per-query slots (+ its bins for wide keys)
-    L.cub = take(L.cub_bytes);
-    const int FS = sp.kind == OMPL_GPU_SPACE_SE3 ? 8 : g.F;
-    L.q32u = take(4ull * nq * FS);
-    L.q32 = take(4ull * nq * FS);
-    L.pd = take(4ull * p.chunks * nq * p.K2);
-    L.pi = take(4ull * p.chunks * nq * p.K2);
-    L.fail = take(4ull * (nq + 1));
-    L.tau = take(8ull * nq);  // the chain cull's shared threshold keys
-    L.total = off;
+    Carver c;
+    L.q = query_layout(c, nq, query_row_width(sp, g));
+    L.pd = c.take(4ull * p.chunks * nq * p.K2);
+    L.pi = c.take(4ull * p.chunks * nq * p.K2);
+    L.fail = c.take(4ull * (nq + 1));
+    L.tau = c.take(8ull * nq);  // the chain cull's shared threshold keys
+    L.total = c.off;
     return L;
 }
 
@@ -2550,9 +2546,9 @@ template <int SP, int F, int K2, int K>
 hipError_t run_fast(const DevSpace &sp, const FastPlan &p, const FastLayout &L, char *ws, const float *f32,
                     const double *f64, uint64_t cap, uint64_t n_end, const SortedStore *ss, const double *qf64,
                     uint32_t nq, uint32_t k, const FastBounds &b, double *od, uint32_t *oi, hipStream_t st) {
-    uint32_t *keys = (uint32_t *)(ws + L.keys), *keys2 = (uint32_t *)(ws + L.keys2);
-    uint32_t *idx = (uint32_t *)(ws + L.idx), *perm = (uint32_t *)(ws + L.perm);
-    float *q32u = (float *)(ws + L.q32u), *q32 = (float *)(ws + L.q32);
+    const QueryBufs q = query_bufs(ws, L.q);
+    uint32_t *keys2 = q.keys2, *perm = q.perm;
+    float *q32 = q.q32;
     float *pd = (float *)(ws + L.pd);
     uint32_t *pi = (uint32_t *)(ws + L.pi);
     uint32_t *fail = (uint32_t *)(ws + L.fail);
@@ -2562,8 +2558,7 @@ hipError_t run_fast(const DevSpace &sp, const FastPlan &p, const FastLayout &L, 
     FastBounds bz = b;  // + the fail count, zeroed by query_rows_kernel
     bz.zero[2] = fail;
     bz.nzero[2] = 1u;
-    hipError_t e = sort_queries<SP, F>(qf64, nq, bz, ss, home_keys, ws + L.cub, L.cub_bytes, q32u, keys, keys2, idx,
-                                       perm, q32, st, (p.cull && ss) ? ss->nodes : nullptr,
+    hipError_t e = sort_queries<SP, F>(qf64, nq, bz, ss, home_keys, q, st, (p.cull && ss) ? ss->nodes : nullptr,
                                        (p.cull && ss) ? ss->kd_tiles : 0u);
     if (e != hipSuccess) return e;
     bool walked = false;
@@ -2633,23 +2628,20 @@ hipError_t run_fast(const DevSpace &sp, const FastPlan &p, const FastLayout &L, 
                            st, f32, cap, n_end, q32, nq, p.chunk_len, w0, (float)sp.w1, sp.dim, pd, pi);
         timer_end(st);
     }
-    if (SP == OMPL_GPU_SPACE_KCHAIN && p.cull) {
-        // the culled chain scan: merge its chunk lists, then the wave certificate (ids, SoA rows)
-        if (p.chunks > 1)
-            hipLaunchKernelGGL((knn_chunk_merge_kernel<K2>), dim3((nq + 3) / 4), b256, 0, st, pd, pi, p.chunks, nq);
+    const bool chain_cull = SP == OMPL_GPU_SPACE_KCHAIN && p.cull;
+    if (chain_cull && p.k2 != K2) return hipErrorInvalidValue;  // fast_plan: the chain's lists are full
+    // the culled chain scan: merge its chunk lists, then the wave certificate (ids, SoA rows)
+    if (chain_cull && p.chunks > 1)
+        hipLaunchKernelGGL((knn_chunk_merge_kernel<K2>), dim3((nq + 3) / 4), b256, 0, st, pd, pi, p.chunks, nq);
+    if (chain_cull || p.chunks == 1) {
         constexpr uint32_t QPB = 256 / K2;
-        if (!ss->rows64) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((knn_certify_wave_kernel<SP, F, K2>), dim3((nq + QPB - 1) / QPB), b256, 0, st, pd, pi, nq,
-                           perm, f64, cap, ss->ids, ss->rows64, qf64, sp, b.absmax, b.qeta + chain_qerr, b.n_live,
-                           (uint32_t)K2, od, oi, k, fail, fail + 1);
-    } else if (p.chunks == 1) {
-        constexpr uint32_t QPB = 256 / K2;
-        // the group walk's lists hold positions in the sorted store (rows64 / ids map them)
+        // the culled walks' lists hold positions in the sorted store (rows64 / ids map them); the
+        // chain's keep all K2 = p.k2 entries, and its 16-bit screen error widens the bound
         const bool pos = walked && p.cull;
         if (pos && !ss->rows64) return hipErrorInvalidValue;
         hipLaunchKernelGGL((knn_certify_wave_kernel<SP, F, K2>), dim3((nq + QPB - 1) / QPB), b256, 0, st, pd, pi, nq,
                            perm, f64, cap, pos ? ss->ids : nullptr, pos ? ss->rows64 : nullptr, qf64, sp, b.absmax,
-                           b.qeta, b.n_live, (uint32_t)p.k2, od, oi, k, fail, fail + 1, 0.f);
+                           b.qeta + chain_qerr, b.n_live, (uint32_t)p.k2, od, oi, k, fail, fail + 1, 0.f);
     } else {
         if (p.cull) return hipErrorInvalidValue;  // position lists need the wave certificate
         if constexpr (K == 64 && SP != OMPL_GPU_SPACE_KCHAIN) {
@@ -2705,31 +2697,18 @@ constexpr int kRadiusGroup = 4;  // 10^7-state radius pass: G=2 2.37 ms, G=4 2.2
 constexpr int kRadiusSlabGroup = 4;
 
 struct RadiusLayout {
-    size_t keys, keys2, idx, perm, cub, q32u, q32, counts, off, scan, total;
-    size_t cub_bytes;
+    QueryLayout q;
+    size_t counts, off, scan, total;
 };
 
 RadiusLayout radius_layout(const DevSpace &sp, const FeatGeom &g, uint32_t nq) {
     RadiusLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t b) {
-        size_t o = off;
-        off += align_up(b);
-        return o;
-    };
-    L.keys = take(4ull * nq);
-    L.keys2 = take(4ull * nq);
-    L.idx = take(4ull * nq);
-    L.perm = take(4ull * nq);
-    L.cub_bytes = home_sort_bytes(nq);  // the counting sort's per-query slots (+ its bins for wide keys)
-    L.cub = take(L.cub_bytes);
-    const int FS = sp.kind == OMPL_GPU_SPACE_SE3 ? 8 : g.F;
-    L.q32u = take(4ull * nq * FS);
-    L.q32 = take(4ull * nq * FS);
-    L.counts = take(8ull * (nq + 1));
-    L.off = take(8ull * (nq + 2));
-    L.scan = take(exclusive_scan_u64_workspace((uint64_t)nq + 1));
-    L.total = off;
+    Carver c;
+    L.q = query_layout(c, nq, query_row_width(sp, g));
+    L.counts = c.take(8ull * (nq + 1));
+    L.off = c.take(8ull * (nq + 2));
+    L.scan = c.take(exclusive_scan_u64_workspace((uint64_t)nq + 1));
+    L.total = c.off;
     return L;
 }
 
@@ -2737,14 +2716,25 @@ template <int SP, int F>
 hipError_t run_radius_fast(const DevSpace &sp, const RadiusLayout &L, char *ws, const double *f64, uint64_t cap,
                            const SortedStore *ss, const double *qf64, uint32_t nq, double r, const FastBounds &b,
                            int phase, uint32_t *out_i, double *out_d, hipStream_t st) {
-    uint32_t *keys = (uint32_t *)(ws + L.keys), *keys2 = (uint32_t *)(ws + L.keys2);
-    uint32_t *idx = (uint32_t *)(ws + L.idx), *perm = (uint32_t *)(ws + L.perm);
-    float *q32u = (float *)(ws + L.q32u), *q32 = (float *)(ws + L.q32);
+    const QueryBufs q = query_bufs(ws, L.q);
     uint64_t *counts = (uint64_t *)(ws + L.counts), *offs = (uint64_t *)(ws + L.off);
-    const dim3 grid((nq + kRadiusGroup - 1) / kRadiusGroup), b64(64);
     if (!ss->rows64) return hipErrorInvalidValue;
     (void)f64;
     (void)cap;
+    // the walk's launch, <G, MODE, Q16> (as types) and the arguments that differ between its forms
+    auto walk = [&](auto G, auto MODE, auto Q16, uint64_t *cnt, const uint64_t *off, uint32_t *oi, double *od,
+                    unsigned long long *counters, uint32_t slab) {
+        hipLaunchKernelGGL((radius32_group_kernel<SP, F, G(), MODE(), Q16()>), dim3((nq + G() - 1) / G()), dim3(64), 0,
+                           st, ss->rows, ss->n_pad, ss->ids, ss->ntiles, ss->tbox, ss->sbox, ss->nsuper, ss->mbox,
+                           ss->nmega, q.q32, q.perm, nq, ss->rows64, qf64, sp, b.absmax, b.qeta, r, cnt, off, oi, od,
+                           counters, slab, Q16() ? ss->rows16 : nullptr, Q16() ? ss->q16 : Q16Geo{},
+                           Q16() ? se3_q16_error(sp, ss->q16) : 0.0);
+    };
+    using GroupG = std::integral_constant<int, kRadiusGroup>;
+    using SlabG = std::integral_constant<int, kRadiusSlabGroup>;
+    using Count = std::integral_constant<int, 0>;
+    using Fill = std::integral_constant<int, 1>;
+    using Slab = std::integral_constant<int, 2>;
     hipError_t e;
     if (phase == 2 && (b.slab == 0 || !out_i || !out_d)) return hipErrorInvalidValue;
     if (phase == 0 || phase == 2) {
@@ -2752,42 +2742,29 @@ hipError_t run_radius_fast(const DevSpace &sp, const RadiusLayout &L, char *ws, 
         FastBounds bz = b;  // + the walk's candidate total, zeroed by query_rows_kernel
         bz.zero[2] = (uint32_t *)(counts + nq);
         bz.nzero[2] = 2u;
-        if ((e = sort_queries<SP, F>(qf64, nq, bz, ss, home_keys, ws + L.cub, L.cub_bytes, q32u, keys, keys2, idx, perm,
-                                     q32, st, ss->nodes, ss->kd_tiles)) != hipSuccess)
+        if ((e = sort_queries<SP, F>(qf64, nq, bz, ss, home_keys, q, st, ss->nodes, ss->kd_tiles)) != hipSuccess)
             return e;
         if (phase == 2) {
             timer_begin(st, "radius32_group_kernel");
-            const dim3 gs((nq + kRadiusSlabGroup - 1) / kRadiusSlabGroup);
             bool q16 = false;
             if constexpr (SP == OMPL_GPU_SPACE_SE3) {
                 if (ss->rows16 && ss->gen16 == ss->gen) {
                     q16 = true;
-                    hipLaunchKernelGGL((radius32_group_kernel<SP, F, kRadiusSlabGroup, 2, true>), gs, b64, 0, st,
-                                       ss->rows, ss->n_pad, ss->ids, ss->ntiles, ss->tbox, ss->sbox, ss->nsuper, ss->mbox, ss->nmega, q32,
-                                       perm, nq, ss->rows64, qf64, sp, b.absmax, b.qeta, r, counts, nullptr, out_i,
-                                       out_d, ss->counters, b.slab, ss->rows16, ss->q16, se3_q16_error(sp, ss->q16));
+                    walk(SlabG{}, Slab{}, std::true_type{}, counts, nullptr, out_i, out_d, ss->counters, b.slab);
                 }
             }
-            if (!q16)
-                hipLaunchKernelGGL((radius32_group_kernel<SP, F, kRadiusSlabGroup, 2>), gs, b64, 0, st, ss->rows,
-                                   ss->n_pad, ss->ids, ss->ntiles, ss->tbox, ss->sbox, ss->nsuper, ss->mbox, ss->nmega, q32, perm, nq,
-                                   ss->rows64, qf64, sp, b.absmax, b.qeta, r, counts, nullptr, out_i, out_d,
-                                   ss->counters, b.slab);
+            if (!q16) walk(SlabG{}, Slab{}, std::false_type{}, counts, nullptr, out_i, out_d, ss->counters, b.slab);
             timer_end(st);
-            hipLaunchKernelGGL((radius_slab_exact_kernel<SP, F>), dim3(nq), b64, 0, st, ss->rows64, ss->ids, qf64, sp,
-                               r, b.slab, counts, out_i, out_d);
+            hipLaunchKernelGGL((radius_slab_exact_kernel<SP, F>), dim3(nq), dim3(64), 0, st, ss->rows64, ss->ids, qf64,
+                               sp, r, b.slab, counts, out_i, out_d);
         } else {
-            hipLaunchKernelGGL((radius32_group_kernel<SP, F, kRadiusGroup, 0>), grid, b64, 0, st, ss->rows, ss->n_pad,
-                               ss->ids, ss->ntiles, ss->tbox, ss->sbox, ss->nsuper, ss->mbox, ss->nmega, q32, perm, nq, ss->rows64, qf64,
-                               sp, b.absmax, b.qeta, r, counts, nullptr, nullptr, nullptr, nullptr, 0u);
+            walk(GroupG{}, Count{}, std::false_type{}, counts, nullptr, nullptr, nullptr, nullptr, 0u);
         }
         // offsets (offs[nq] = the total) and the longest segment (offs[nq + 1])
         return launch_exclusive_scan_u64(counts, (uint64_t)nq, offs, ws + L.scan, st, offs + nq + 1);
     }
     timer_begin(st, "radius32_group_kernel");
-    hipLaunchKernelGGL((radius32_group_kernel<SP, F, kRadiusGroup, 1>), grid, b64, 0, st, ss->rows, ss->n_pad,
-                       ss->ids, ss->ntiles, ss->tbox, ss->sbox, ss->nsuper, ss->mbox, ss->nmega, q32, perm, nq, ss->rows64, qf64, sp,
-                       b.absmax, b.qeta, r, nullptr, offs, out_i, out_d, ss->counters, 0u);
+    walk(GroupG{}, Fill{}, std::false_type{}, nullptr, offs, out_i, out_d, ss->counters, 0u);
     timer_end(st);
     return hipGetLastError();
 }
@@ -3685,7 +3662,8 @@ hipError_t sorted_alloc(SortedStore *s, uint32_t pad_tiles, uint32_t max_nodes, 
         if ((e = grow_array(&s->tkey0, dummy, (size_t)pad_tiles)) != hipSuccess) return e;
         dummy = 0;
         if ((e = grow_array(&s->qcount, dummy, home_bins_words(pad_tiles))) != hipSuccess) return e;
-        // the home-key bins are zero between calls (home_bins_scan_kernel re-zeroes what it reads)
+        // the home-key bins keep this capacity's layout (pad_tiles = cap_pos / kCullTile, as sort_queries
+        // reads it) until the next reallocation and are zero between calls (the scan re-zeroes what it reads)
         if ((e = hipMemsetAsync(s->qcount, 0, 4 * home_bins_words(pad_tiles), st)) != hipSuccess) return e;
         s->cap_pos = n_pad;
         hipLaunchKernelGGL(iota_kernel, dim3((pad_tiles + 255) / 256), dim3(256), 0, st, s->tkey0, pad_tiles);
@@ -3733,21 +3711,17 @@ hipError_t build_sorted(const float *f32, const double *f64, uint64_t cap, uint6
                              (uint32_t *)nullptr, n, st)) != hipSuccess)
         return e;
     const size_t row_bytes = std::max<size_t>(4ull * RW * nl, 4ull * fa * n);  // each half of the pair
-    size_t off = 0;
-    auto take = [&](size_t b) {
-        const size_t o = off;
-        off += align_up(b);
-        return o;
-    };
-    const size_t o_flags = take(n), o_sel = take(4 * n), o_k0 = take(4ull * nl), o_w = take(2 * row_bytes),
-                 o_tb = take(4ull * main_tiles * 2 * NB), o_ns = take(16ull * main_tiles + 16), o_cnt = take(8),
-                 o_tmp = take(tmp_sel);
+    Carver c;
+    const size_t o_flags = c.take(n), o_sel = c.take(4 * n), o_k0 = c.take(4ull * nl), o_w = c.take(2 * row_bytes),
+                 o_tb = c.take(4ull * main_tiles * 2 * NB), o_ns = c.take(16ull * main_tiles + 16), o_cnt = c.take(8),
+                 o_tmp = c.take(tmp_sel);
     // median partition: bin counts per node of the deepest global level, children's boxes,
     // per-node selections, per-chunk counts
     const size_t nodes_max = Lg > 0 ? (size_t)1 << (Lg - 1) : 1;
-    const size_t o_h = take(4ull * kPartBins * nodes_max), o_cb = take(4ull * 2 * NB * 2 * nodes_max),
-                 o_ps = take(8ull * nodes_max), o_pc = take(8ull * (nodes_max + main_tiles / (kPartChunk / kCullTile) + 2));
-    if ((e = scratch_ensure(s, off)) != hipSuccess) return e;
+    const size_t o_h = c.take(4ull * kPartBins * nodes_max), o_cb = c.take(4ull * 2 * NB * 2 * nodes_max),
+                 o_ps = c.take(8ull * nodes_max),
+                 o_pc = c.take(8ull * (nodes_max + main_tiles / (kPartChunk / kCullTile) + 2));
+    if ((e = scratch_ensure(s, c.off)) != hipSuccess) return e;
     char *w = (char *)s->scratch;
     uint8_t *flags = (uint8_t *)(w + o_flags);
     uint32_t *sel = (uint32_t *)(w + o_sel), *nsel = (uint32_t *)(w + o_cnt);
@@ -3862,15 +3836,10 @@ hipError_t append_sorted(const float *f32, const double *f64, uint64_t cap, uint
     const uint32_t n_tail = (uint32_t)n_tail64;
     if (n_tail == 0) return hipSuccess;
     const size_t cub = home_sort_bytes(n_tail);
-    size_t off = 0;
-    auto take = [&](size_t bb) {
-        const size_t o = off;
-        off += align_up(bb);
-        return o;
-    };
-    const size_t o_k0 = take(4ull * n_tail), o_k1 = take(4ull * n_tail), o_i0 = take(4ull * n_tail),
-                 o_i1 = take(4ull * n_tail), o_cub = take(cub);
-    if ((e = scratch_ensure(s, off)) != hipSuccess) return e;
+    Carver c;
+    const size_t o_k0 = c.take(4ull * n_tail), o_k1 = c.take(4ull * n_tail), o_i0 = c.take(4ull * n_tail),
+                 o_i1 = c.take(4ull * n_tail), o_cub = c.take(cub);
+    if ((e = scratch_ensure(s, c.off)) != hipSuccess) return e;
     char *w = (char *)s->scratch;
     uint32_t *k0 = (uint32_t *)(w + o_k0), *k1 = (uint32_t *)(w + o_k1);
     uint32_t *i0 = (uint32_t *)(w + o_i0), *i1 = (uint32_t *)(w + o_i1);

@@ -88,6 +88,42 @@ def test_rebuild_when_tail_full_or_many_removed(gpu):
     assert b2 == 3                          # half the states removed: rebuilt
 
 
+def test_home_bins_survive_shrink_then_regrow(gpu):
+    """The query sort's persistent bins are laid out once for the store's tile capacity, so rebuilds
+    that move the k-d tile count across a multiple of 1,024 inside one allocation (1,250 tiles ->
+    782 after removals -> 1,094 after regrowth, capacity 1,440) never read an earlier call's prefix
+    words as counts: every kNN and radius answer along the way equals the oracle's."""
+    sp = RealVectorStateSpace(4)
+    rng = np.random.default_rng(17)
+    data = rng.uniform(0, 1, (80000, 4))
+    more = rng.uniform(0, 1, (20000, 4))
+    q = rng.uniform(0, 1, (2000, 4))
+    allx = np.concatenate([data, more])
+    nn = NearestNeighborsGPU(sp, gpu)
+
+    def check(keep, builds):
+        ids, d, _ = nn.nearestKBatch(q, 8)
+        oi, od, _ = O.knn(sp, allx[keep], q, 16)
+        assert_knn_parity(ids, d, keep[oi], od, 8)
+        assert nn.index_stats()[0] == builds
+
+    nn.add(data)                           # 1,250 tiles: two 1,024-bin blocks
+    check(np.arange(80000), 1)
+    for i in range(30000):                 # more than a quarter gone: rebuild, 782 tiles, one block
+        assert nn.remove(i)
+    check(np.arange(30000, 80000), 2)
+    nn.add(more)                           # past the 8,192-state tail: rebuild, 1,094 tiles, two blocks
+    keep = np.arange(30000, 100000)
+    check(keep, 3)
+    r = 0.06                               # ~4 neighbours per query
+    off, rid, rd = nn.nearestRBatch(q[:200], r)
+    ooff, oid, od = O.radius(sp, allx[keep], q[:200], r)
+    np.testing.assert_array_equal(off, ooff)
+    np.testing.assert_array_equal(rid.astype(np.int64), keep[oid.astype(np.int64)])
+    np.testing.assert_array_equal(rd, od)
+    assert nn.index_stats()[0] == 3
+
+
 def test_device_rrt_growth_feeds_the_tail(gpu):
     """States appended on the device by the RRT loop are placed in the tail at the next batched
     query (no host copy of the store)."""

@@ -1,4 +1,4 @@
-"""Fit of chord_theta's polynomial (ompl_amd/csrc/knn_fast_impl.h): theta = 2 asin(c / 2) =
+"""Fit of chord_theta's polynomial (ompl_amd/csrc/feat_dist.h): theta = 2 asin(c / 2) =
 c (1 + x R(x)), x = c^2 / 4 in [0, 0.5].  Lawson-reweighted least squares for a minimax fit of
 the error on theta; prints the coefficients (low order first) and the largest error in fp64 and
 with fp32 Horner evaluation.  Run: python tools/fit_asin.py [degree]"""
